@@ -1,7 +1,13 @@
 """Benchmark: env-steps/sec of the batched Sokoban rollout (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N ... bench.py --gpus N      (one rank per GPU)
+
+A plain run sets up, warms up, times exactly --steps rollouts, checks that every replayed
+rollout wrote the same record, writes the last timed rollout's outputs when --dump-outputs is
+given, and prints the result line.  Every other leg described below (roofline of the dominant
+kernel, eager rate, advantage / toytext / API / text legs, the at-scale leg, the CPU baselines,
+repeated trials, the N>1 placement variants) runs only with --full.
 
 Workload (BASELINE.json configs[2], SURVEY §8(d) "SK"): Sokoban 6x6 / 1 box, 8192 envs per
 GPU (512 groups x 16, env i seeded 1000 + i // 16), 5 turns of up to K=5 synthetic actions
@@ -16,7 +22,7 @@ Multi-GPU: weak scaling — every rank runs its own 8192 envs (global group ids 
 rank r seeds groups r*512..), no collective on the data path; value = all ranks' env steps
 / max-over-ranks time.
 
-Also reported: roofline of the dominant kernel (rmi_sokoban_step_turn) — algorithmic bytes
+Reported with --full: roofline of the dominant kernel (rmi_sokoban_step_turn) — algorithmic bytes
 (141 B per active env-turn) over the average launch duration measured with HIP
 events around back-to-back launches — PMC HBM traffic per launch from the committed
 rocprofv3 pass (profiles/), and the CPU baseline (the oracle's per-env Python port of the
@@ -1189,14 +1195,58 @@ def check_gathered(own, gathered, world, rank, distinct=True):
     return bool(ok)
 
 
+def rollout_outputs(R, ep):
+    """What a caller of Rollout.step() holds after it: the episode record `ep` the rollout wrote
+    (every field of its arena), the env state it left, and the fused finalize's outputs (the
+    normalised trajectory scores and the get_rollout_states metrics).  -> {name: host array,
+    float32 (float64 for the f64 fields)}; about 2.6 MB in all at the bench's 8192 envs, so
+    nothing is sampled.  Every array is finite: the metrics are NaN where the reference divides
+    by zero turns, so `metrics` carries 0 in those cells and `metrics_nonfinite` says what stood
+    there (0 finite, 1 NaN, 2 +inf, 3 -inf); a non-finite value anywhere else is an error."""
+    e = R.env
+    t = {"num_actions": ep.num_actions, "flags": ep.flags, "n_turns": ep.n_turns, "penalty": ep.penalty,
+         "turn_reward": ep.turn_reward, "turn_info": ep.turn_info, "turn_exec": ep.turn_exec,
+         "room_state": e.room_state, "player": e.player, "num_env_steps": e.num_env_steps,
+         "boxes_on_target": e.boxes_on_target, "normalized_score": R.norm, "metrics": R.metrics}
+    out = {k: v.detach().cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32)
+           for k, v in t.items()}
+    out["metrics"], out["metrics_nonfinite"] = split_nonfinite(out["metrics"])
+    for k, a in out.items():
+        if not np.isfinite(a).all():
+            raise RuntimeError(f"rollout output {k} is not finite")
+    return out
+
+
+def split_nonfinite(a):
+    """A float array that may hold NaN or +-inf -> (the array with 0 in those cells, f32 codes of
+    what stood there: 0 finite, 1 NaN, 2 +inf, 3 -inf); lossless, and both parts finite."""
+    code = np.zeros(a.shape, np.float32)
+    code[np.isnan(a)] = 1
+    code[np.isposinf(a)] = 2
+    code[np.isneginf(a)] = 3
+    return np.where(code == 0, a, 0).astype(a.dtype), code
+
+
+def dump_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=40)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg: repeated trials, the dominant kernel's roofline, "
+                         "the eager rate, the extras, the CPU baselines and (N>1) the placement variants")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed rollout computed (rank 0) as DIR/<name>.npy")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the advantage leg and the copy-peak probe")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the advantage, toytext, API, text and at-scale legs and the copy probe")
     ap.add_argument("--group", type=int, default=8, help="rollouts per graph replay (reduced to divide --steps)")
     ap.add_argument("--exchange", choices=("serial", "overlap", "auto"), default="serial",
                     help="N>1: the all-gather serial after its rollouts on the same stream (StarPO: the gathered "
@@ -1441,12 +1491,17 @@ def main():
             el = float(t.item())
         return el
 
-    # the --steps loop repeated until >= 1000 rollouts and >= 0.2 s were timed; the median
-    # trial is reported (a 20-step trial is ~0.5 ms: one trial alone is noise)
-    trials = [timed_trial()]
-    while len(trials) < 200 and (len(trials) * args.steps < 1000 or sum(trials) < 0.2):
+    # the headline: exactly --steps rollouts, timed once
+    elapsed = timed_trial()
+    outputs = None
+    if args.dump_outputs and rank == 0:  # read back before any later leg steps the env again
+        last = eps[(((count[0] - G) // G) & 1) * G + G - 1] if graph is not None else R.env.ep
+        outputs = rollout_outputs(R, last)
+    # --full: the same loop repeated until >= 1000 rollouts and >= 0.2 s were timed, for the
+    # spread of a trial (a 20-step trial is ~0.5 ms); reported beside the headline in `timing`
+    trials = [elapsed]
+    while args.full and len(trials) < 200 and (len(trials) * args.steps < 1000 or sum(trials) < 0.2):
         trials.append(timed_trial())
-    elapsed = float(np.median(trials))
     total_steps = steps_per_rollout * args.steps
     if dist:
         c = torch.tensor([total_steps], dtype=torch.float64, device=device)
@@ -1490,45 +1545,51 @@ def main():
         exchange_ok = bool(ok_t.item())
         if not exchange_ok:
             raise RuntimeError("replayed rollouts / gathered arenas do not match")
-        if dist:  # every placement timed beside the headline (collective: every rank)
+        if dist and args.full:  # every placement timed beside the headline (collective: every rank)
             variants = variants_fn()
 
-    # ---- dominant-kernel roofline: HIP events around the turn launches (eager, same stream)
-    n_prof = min(args.steps, 50)
-    events = [R.timed_turns() for _ in range(n_prof)]
-    torch.cuda.synchronize()
-    durs = np.array([a.elapsed_time(b) for a, b in events]) * 1e-3  # s per rollout's T launches
-    bytes_per_rollout = float(np.sum(active_per_turn)) * BYTES_PER_ENV_TURN
-    achieved = bytes_per_rollout * n_prof / float(durs.sum()) / 1e9  # GB/s
-    avg_launch_us = float(durs.mean() / T_TURNS * 1e6)
-    traffic = _pmc_field(PMC_GLOB, "hbm_bytes_per_launch")
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
 
-    # eager (no graph) rate, for reference
-    eager_steps = 20
-    torch.cuda.synchronize()
-    te = time.perf_counter()
-    for _ in range(eager_steps):
-        R.step()
-    torch.cuda.synchronize()
-    eager_ms = (time.perf_counter() - te) / eager_steps * 1e3
+    # ---- everything below the headline runs with --full only
+    bytes_per_rollout = float(np.sum(active_per_turn)) * BYTES_PER_ENV_TURN
+    achieved = avg_launch_us = eager_ms = None
+    if args.full:
+        # dominant-kernel roofline: HIP events around the turn launches (eager, same stream)
+        n_prof = min(args.steps, 50)
+        events = [R.timed_turns() for _ in range(n_prof)]
+        torch.cuda.synchronize()
+        durs = np.array([a.elapsed_time(b) for a, b in events]) * 1e-3  # s per rollout's T launches
+        achieved = bytes_per_rollout * n_prof / float(durs.sum()) / 1e9  # GB/s
+        avg_launch_us = float(durs.mean() / T_TURNS * 1e6)
+
+        # eager (no graph) rate, for reference
+        eager_steps = 20
+        torch.cuda.synchronize()
+        te = time.perf_counter()
+        for _ in range(eager_steps):
+            R.step()
+        torch.cuda.synchronize()
+        eager_ms = (time.perf_counter() - te) / eager_steps * 1e3
+    traffic = _pmc_field(PMC_GLOB, "hbm_bytes_per_launch")
 
     # the extras (and the CPU baselines below) run on rank 0 only: the other ranks' GPUs hold
     # identical work, and the headline above is already timed
-    extras = not args.no_extras and rank == 0
+    extras = args.full and not args.no_extras and rank == 0
     adv = advantage_leg(R, device) if extras else None
     copy_probe = hbm_copy_peak(device) if extras else None
     # frac_of_achievable's denominator: the larger of this box's probe and the guide's measured
     # float4 copy (MI355X_MICROARCH.md: 6.29 TB/s), so a slow probe never inflates the fraction
     copy_peak = max(copy_probe, GUIDE_COPY_GBS) if copy_probe else None
     toytext = toytext_legs(device) if extras else None
-    api = api_leg(device) if not args.no_extras and rank == 0 else None
-    text = text_leg(R, device) if not args.no_extras and rank == 0 else None
+    api = api_leg(device) if extras else None
+    text = text_leg(R, device) if extras else None
     if text is not None and api is not None:  # the caller path's text kernels (measured in api_leg)
         text["prompt"] = api.pop("prompt_kernels", None)
     if text is not None:
         attach_issue_fracs(text)
     at_scale = None
-    if not args.no_extras and rank == 0:
+    if extras:
         s_dur, s_B = scale_leg(R, device)
         s_bytes = bytes_per_rollout * (s_B // R.B)
         s_ach = s_bytes / s_dur / 1e9
@@ -1552,7 +1613,7 @@ def main():
 
     if rank == 0:
         cpu = cpu_par = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 cpu = cpu_baseline(R)
             except Exception as ex:  # the baseline must never break the bench line
@@ -1577,10 +1638,14 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
+            "full": args.full,
             "timing": {"trials": len(trials), "rollouts_timed": len(trials) * args.steps,
-                       "seconds_timed": float(np.sum(trials)), "statistic": "median trial",
-                       "ms_per_step_min_med_max": [min(trials) / args.steps * 1e3, elapsed / args.steps * 1e3,
+                       "seconds_timed": float(np.sum(trials)),
+                       "statistic": "the first trial: exactly --steps rollouts (later trials: --full, spread only)",
+                       "ms_per_step_min_med_max": [min(trials) / args.steps * 1e3,
+                                                   float(np.median(trials)) / args.steps * 1e3,
                                                    max(trials) / args.steps * 1e3]},
+            "outputs_dumped": sorted(outputs) if outputs is not None else None,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -1595,12 +1660,12 @@ def main():
                        "exchange_transport": transport, "exchange_transport_note": xg_note,
                        "rollouts_per_gather": (G if exchange_mode == "overlap" else P) if dist else None},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
                          "traffic_source": _pmc_source(PMC_GLOB),
                          "achievable_peak": copy_peak,
                          "achievable_peak_probe": copy_probe, "achievable_peak_guide": GUIDE_COPY_GBS,
                          "achievable_peak_rule": "max(probe on this box, guide's float4 copy)",
-                         "frac_of_achievable": (achieved / copy_peak) if copy_peak else None,
+                         "frac_of_achievable": (achieved / copy_peak) if achieved and copy_peak else None,
                          "kernel": "rmi_sokoban_step_turn", "avg_launch_us": avg_launch_us,
                          "bytes_per_env_turn": BYTES_PER_ENV_TURN, "active_envs_per_turn": active_per_turn,
                          "timed_region": {

@@ -130,6 +130,26 @@ def test_exchange_default_is_a_serial_gather_per_rollout():
         raise AssertionError(f"exchange_plan accepted --rollouts-per-gather {bad[0]} for G={bad[1]}")
 
 
+def test_plain_run_is_the_default_and_dump_writes_float_arrays(tmp_path):
+    """--full is off unless asked for; --dump-outputs takes a directory, and dump_outputs writes one
+    .npy per named array."""
+    import numpy as np
+    args = bench.make_parser().parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 3
+    args = bench.make_parser().parse_args(["--full", "--dump-outputs", str(tmp_path / "d")])
+    assert args.full is True and args.dump_outputs == str(tmp_path / "d")
+    val, code = bench.split_nonfinite(np.array([np.nan, 1.5, np.inf, -np.inf, 0.0]))
+    assert val.dtype == np.float64 and val.tolist() == [0.0, 1.5, 0.0, 0.0, 0.0]
+    assert code.dtype == np.float32 and code.tolist() == [1.0, 0.0, 2.0, 3.0, 0.0]
+    arrays = {"a": np.arange(6, dtype=np.float32).reshape(2, 3), "b": val}
+    bench.dump_outputs(args.dump_outputs, arrays)
+    assert sorted(os.listdir(args.dump_outputs)) == ["a.npy", "b.npy"]
+    for k, v in arrays.items():
+        got = np.load(os.path.join(args.dump_outputs, k + ".npy"), allow_pickle=False)
+        assert got.dtype == v.dtype
+        np.testing.assert_array_equal(got, v)
+
+
 def _serial_worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)

@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-abadv}; VAR=$2; mkdir -p $OUT
 for i in 1 2; do
   for v in default $VAR; do
     if [ $v = default ]; then L=""; else L=variants/libragen_amd_$v.so; fi
-    RAGEN_AMD_LIB=$L timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/$v.$i.log 2>&1 || exit 1
+    RAGEN_AMD_LIB=$L timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/$v.$i.log 2>&1 || exit 1
     python3 - $OUT/$v.$i.log $v <<'PY'
 import json, sys
 l = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); a = l["advantage"]

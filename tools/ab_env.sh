@@ -9,10 +9,10 @@ for i in 1 2 3; do
   for e in - "$@"; do
     tag=$(echo "$e" | tr '=' '_')
     if [ "$e" = - ]; then
-      timeout -k 10 240 python bench.py --no-extras --no-cpu-baseline > $OUT/$tag.$i.json 2>> $OUT/err.log || exit 1
+      timeout -k 10 240 python bench.py --full --no-extras --no-cpu-baseline > $OUT/$tag.$i.json 2>> $OUT/err.log || exit 1
     else
       export "$e"
-      timeout -k 10 240 python bench.py --no-extras --no-cpu-baseline > $OUT/$tag.$i.json 2>> $OUT/err.log || exit 1
+      timeout -k 10 240 python bench.py --full --no-extras --no-cpu-baseline > $OUT/$tag.$i.json 2>> $OUT/err.log || exit 1
       unset "${e%%=*}"
     fi
     python -c "import json;d=json.load(open('$OUT/$tag.$i.json'));print('$e', round(d['ms_per_step']*1e3, 2), round(d['roofline']['avg_launch_us'], 3))" | tee -a $OUT/ab.txt

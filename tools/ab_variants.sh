@@ -9,7 +9,7 @@ for i in 1 2; do
   (cd tools/_build/r01 && timeout -k 10 300 python bench.py --steps 1000 --warmup 40 --no-cpu-baseline --no-extras) \
     > $OUT/r01_$i.log 2>&1 || { echo r01 failed; tail -5 $OUT/r01_$i.log; exit 1; }
   for v in $VARS; do
-    RAGEN_AMD_LIB=$PWD/tools/_build/libragen_amd_$v.so timeout -k 10 300 python bench.py --steps 1000 --warmup 40 \
+    RAGEN_AMD_LIB=$PWD/tools/_build/libragen_amd_$v.so timeout -k 10 300 python bench.py --full --steps 1000 --warmup 40 \
       --no-cpu-baseline --no-extras > $OUT/${v}_$i.log 2>&1 || { echo $v failed; tail -5 $OUT/${v}_$i.log; exit 1; }
   done
 done

@@ -31,7 +31,7 @@ for s in $STEPS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
       ok_or_stop $? smoke; tail -3 "$OUT/smoke.log";;
     bench)
-      timeout -k 10 600 python bench.py > "$OUT/bench.log" 2>&1
+      timeout -k 10 600 python bench.py --full > "$OUT/bench.log" 2>&1
       ok_or_stop $? bench; tail -2 "$OUT/bench.log";;
     prof)  # the headline path only: its kernel averages are the bench line's
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o bench --output-format csv \
@@ -39,12 +39,12 @@ for s in $STEPS; do
       ok_or_stop $? prof; tail -2 "$OUT/prof.log";;
     prof_all)  # every leg (advantage, toy-text, text API, at-scale) for the extras' kernels
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_all" -o bench --output-format csv \
-        -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline > "$OUT/prof_all.log" 2>&1
+        -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline > "$OUT/prof_all.log" 2>&1
       ok_or_stop $? prof_all; tail -2 "$OUT/prof_all.log";;
     pmc)
       for c in FETCH_SIZE WRITE_SIZE; do
         timeout -k 10 600 rocprofv3 --pmc $c --kernel-trace -d "$OUT/pmc_$c" -o pmc --output-format csv \
-          -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-graph > "$OUT/pmc_$c.log" 2>&1
+          -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-graph > "$OUT/pmc_$c.log" 2>&1
         ok_or_stop $? "pmc_$c"
       done;;
     *)

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 TAG=${1:-r02s}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 step() { echo "[$1] rc=$2" | tee -a $OUT/status.txt; if [ "$2" -ne 0 ]; then exit "$2"; fi; }
-timeout -k 10 600 python bench.py > $OUT/bench.log 2>&1; step bench $?
+timeout -k 10 600 python bench.py --full > $OUT/bench.log 2>&1; step bench $?
 tail -c 600 $OUT/bench.log
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv \
   -- python3 bench.py --steps 1000 --warmup 40 --no-cpu-baseline --no-extras > $OUT/prof.log 2>&1; step prof $?

@@ -13,12 +13,12 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -v -p no:cacheprovider --timeout 200 --timeout-method thread > $OUT/pytest_gpu.log 2>&1; step pytest $?
   tail -2 $OUT/pytest_gpu.log
 fi
-timeout -k 10 400 python bench.py > $OUT/bench.log 2>&1; step bench $?
+timeout -k 10 400 python bench.py --full > $OUT/bench.log 2>&1; step bench $?
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv \
   -- python3 bench.py --steps 200 --warmup 40 --no-cpu-baseline --no-extras > $OUT/prof.log 2>&1; step prof $?
 python3 tools/trace_reconcile.py $OUT/prof $OUT/prof.log $OUT/trace_reconcile.json > /dev/null; step reconcile $?
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/prof_all -o all --output-format csv \
-  -- python3 bench.py --no-cpu-baseline > $OUT/prof_all.log 2>&1; step prof_all $?
+  -- python3 bench.py --full --no-cpu-baseline > $OUT/prof_all.log 2>&1; step prof_all $?
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 120 rocprofv3 --pmc $c --kernel-trace -d $OUT/sk_$c -o pmc --output-format csv \
     -- python3 tools/prof_sokoban.py --reps 20 > $OUT/sk_$c.log 2>&1; step "sokoban $c" $?

@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --t
 tail -3 $OUT/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; step smoke $?
 if [ "${SKIP_BENCH:-0}" = "0" ]; then
-  timeout -k 10 400 python bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; step bench $?
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 ${BENCH_ARGS:-} > $OUT/bench.log 2>&1; step bench $?
   tail -1 $OUT/bench.log | cut -c1-400
 fi
 echo session-done

@@ -18,7 +18,7 @@ tail -1 $OUT/torchrun1.log
 timeout -k 10 200 python bench.py --double-buffer --steps 40 --warmup 8 --no-extras --no-cpu-baseline > $OUT/dbuf.log 2>&1; step dbuf $?
 tail -1 $OUT/dbuf.log
 if [ "${SKIP_BENCH:-0}" = "0" ]; then
-  timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $OUT/bench.log 2>&1; step bench $?
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.log 2>&1; step bench $?
   tail -1 $OUT/bench.log
 fi
 echo session-done

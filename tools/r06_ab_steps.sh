@@ -9,7 +9,7 @@ step() { echo "[$1] rc=$2" | tee -a $OUT/status.txt; if [ "$2" -ne 0 ]; then exi
 for rep in 1 2; do
   for v in new old; do
     if [ $v = old ]; then export RAGEN_AMD_LIB=$PWD/variants/libragen_amd_oldsk.so; else unset RAGEN_AMD_LIB; fi
-    timeout -k 10 240 python bench.py --no-extras --no-cpu-baseline > $OUT/bench_${v}_$rep.json 2> $OUT/bench_${v}_$rep.err; step bench_${v}_$rep $?
+    timeout -k 10 240 python bench.py --full --no-extras --no-cpu-baseline > $OUT/bench_${v}_$rep.json 2> $OUT/bench_${v}_$rep.err; step bench_${v}_$rep $?
     python -c "import json;d=json.load(open('$OUT/bench_${v}_$rep.json'));print('$v', d['ms_per_step'], d['roofline']['avg_launch_us'])" | tee -a $OUT/ab.txt
   done
 done

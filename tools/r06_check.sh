@@ -13,11 +13,11 @@ if [ -n "$TESTS" ]; then
   tail -3 $OUT/pytest_gpu.log
 fi
 if [ "${BENCH:-0}" = "1" ]; then
-  timeout -k 10 300 python bench.py --no-extras --no-cpu-baseline > $OUT/bench_noextras.json 2> $OUT/bench_noextras.err; step bench $?
+  timeout -k 10 300 python bench.py --full --no-extras --no-cpu-baseline > $OUT/bench_noextras.json 2> $OUT/bench_noextras.err; step bench $?
   python -c "import json;d=json.load(open('$OUT/bench_noextras.json'));print({k:d[k] for k in ('value','ms_per_step')}, d['roofline']['avg_launch_us'])"
 fi
 if [ "${DB:-0}" = "1" ]; then
-  timeout -k 10 300 python bench.py --no-extras --no-cpu-baseline --double-buffer > $OUT/bench_db.json 2> $OUT/bench_db.err; step bench_db $?
+  timeout -k 10 300 python bench.py --full --no-extras --no-cpu-baseline --double-buffer > $OUT/bench_db.json 2> $OUT/bench_db.err; step bench_db $?
   python -c "import json;d=json.load(open('$OUT/bench_db.json'));print({k:d[k] for k in ('value','ms_per_step','exchange_variants_ms_per_rollout','gathered')}, d['config']['exchange_transport'])"
 fi
 echo session-done
