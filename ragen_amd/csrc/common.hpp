@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/ragen_amd.h"
 
 #define RMI_API extern "C" __attribute__((visibility("default")))
@@ -79,6 +81,37 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Kernel-argument values pinned at this point of the program.  The empty asm takes each value in
+// an SGPR and hands it back, so the argument's scalar load is issued and waited for here and the
+// value the kernel goes on with is the asm's result: a kernel that pins all the arguments of its
+// regular path at its entry fetches them in one batch behind one wait, and the compiler can
+// neither sink a load to the argument's first use (behind a wait of its own there) nor fetch the
+// argument a second time when registers run short (it moves such a value to a VGPR lane
+// instead).  A pointer comes back as a global-memory address, which a kernel argument's pointer
+// is, so accesses through it stay global_load / global_store.
+template <class T>
+__device__ __forceinline__ void arg_pin(T& x) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "a dword or qword argument");
+  if constexpr (std::is_pointer<T>::value) {
+    using E = typename std::remove_pointer<T>::type;
+    uint64_t u = reinterpret_cast<uint64_t>(x);
+    asm volatile("" : "+s"(u));
+    x = (T)(__attribute__((address_space(1))) E*)u;
+  } else if constexpr (sizeof(T) == 8) {
+    uint64_t u = __builtin_bit_cast(uint64_t, x);
+    asm volatile("" : "+s"(u));
+    x = __builtin_bit_cast(T, u);
+  } else {
+    uint32_t u = __builtin_bit_cast(uint32_t, x);
+    asm volatile("" : "+s"(u));
+    x = __builtin_bit_cast(T, u);
+  }
+}
+template <class... T>
+__device__ __forceinline__ void args_pin(T&... x) {
+  (arg_pin(x), ...);
 }
 
 // --------------------------------------------------------------- PCG64 (numpy)
@@ -277,17 +310,26 @@ constexpr int kFinT = 8;  // turns of the record loaded up front
 struct FinRecord {
   double r[kFinT];
   uint8_t info[kFinT];
+  // Rows k < ep.T only (wave-uniform early exit: T comes with the kernel arguments, so the
+  // branches wait for no load and the loads stay in the turn's one up-front batch).
   template <class Ix = int64_t>
   __device__ __forceinline__ void load(const rmi_episode_t& ep, int64_t bc) {
     const int64_t B = ep.B;
+    const int T = ep.T;
 #pragma unroll
     for (int k = 0; k < kFinT; ++k) {
-      const int64_t t = k < ep.T ? k : ep.T - 1;  // clamped, always valid
-      r[k] = *elem<Ix>(ep.turn_reward + t * B, bc);
-      info[k] = *elem<Ix>(ep.turn_info + t * B, bc);
+      r[k] = 0.0;
+      info[k] = 0;
+    }
+#pragma unroll
+    for (int k = 0; k < kFinT; ++k) {
+      if (k >= T) break;
+      r[k] = *elem<Ix>(ep.turn_reward + k * B, bc);
+      info[k] = *elem<Ix>(ep.turn_info + k * B, bc);
     }
   }
   __device__ __forceinline__ void set(int turn, double acc, uint8_t inf) {
+    if (turn >= kFinT) return;  // (uniform) a later turn's record is not held here
 #pragma unroll
     for (int k = 0; k < kFinT; ++k)
       if (k == turn) {
@@ -311,15 +353,16 @@ __device__ __forceinline__ void finalize_envs(const rmi_episode_t& ep, const rmi
   const int64_t B = ep.B;
   double score = 0.0;  // python sum over the turns, in turn order
   int eff = 0, val = 0, present = 0;
+  const int T = ep.T;
 #pragma unroll
-  for (int k = 0; k < kFinT; ++k)
-    if (k < ep.T) {
-      score += rec.r[k];
-      present |= rec.info[k] & RMI_INFO_PRESENT;
-      eff += (rec.info[k] >> 1) & 1;
-      val += (rec.info[k] >> 2) & 1;
-    }
-  for (int t = kFinT; t < ep.T; ++t) {  // long episodes only
+  for (int k = 0; k < kFinT; ++k) {
+    if (k >= T) break;  // wave-uniform
+    score += rec.r[k];
+    present |= rec.info[k] & RMI_INFO_PRESENT;
+    eff += (rec.info[k] >> 1) & 1;
+    val += (rec.info[k] >> 2) & 1;
+  }
+  for (int t = kFinT; t < T; ++t) {  // long episodes only
     const int64_t bc = b < B ? b : B - 1;
     const bool mine = t == acted_turn;  // written by this launch: use the registers
     const uint8_t inf = mine ? acc_info : *elem<Ix>(ep.turn_info + (int64_t)t * B, bc);
@@ -342,22 +385,25 @@ __device__ __forceinline__ void finalize_envs(const rmi_episode_t& ep, const rmi
     }
   }
   if (!fin.norm) return;
-  const int gs = fin.group_size, method = fin.method;  // uniform; all lanes reach the shuffles
-  const double md = group_sum<LPE>(0.0 + (double)x, gs) / (double)gs;
-  const float mean = (float)md;
-  float sd = 0.0f;
-  if (method == RMI_NORM_MEAN_STD || method == RMI_NORM_ASYM_CLIP) {
-    const double d = (double)x - md;
-    const double q = group_sum<LPE>(0.0 + d * d, gs);
-    sd = gs > 1 ? (float)sqrt(q / (double)(gs - 1)) : __builtin_nanf("");
-  }
-  const bool use = sd > 1e-6f;
+  // wave-uniform on the method, so all lanes reach the shuffles a method needs and no method pays
+  // for a reduction it does not use: IDENTITY none (and no divide), MEAN one, the others two
+  const int gs = fin.group_size, method = fin.method;
   float y;
-  if (method == RMI_NORM_IDENTITY) y = x;
-  else if (method == RMI_NORM_MEAN) y = x - mean;
-  else {
-    y = use ? (x - mean) / (sd + 1e-6f) : 0.0f;
-    if (method == RMI_NORM_ASYM_CLIP) y = fminf(fmaxf(y, -1.0f), 3.0f);
+  if (method == RMI_NORM_IDENTITY) {
+    y = x;
+  } else {
+    const double md = group_sum<LPE>(0.0 + (double)x, gs) / (double)gs;
+    const float mean = (float)md;
+    if (method == RMI_NORM_MEAN) {
+      y = x - mean;
+    } else {
+      const double d = (double)x - md;
+      const double q = group_sum<LPE>(0.0 + d * d, gs);
+      const float sd = gs > 1 ? (float)sqrt(q / (double)(gs - 1)) : __builtin_nanf("");
+      const bool use = sd > 1e-6f;
+      y = use ? (x - mean) / (sd + 1e-6f) : 0.0f;
+      if (method == RMI_NORM_ASYM_CLIP) y = fminf(fmaxf(y, -1.0f), 3.0f);
+    }
   }
   if (writer) *elem<Ix>(fin.norm, b) = y;
 }

@@ -604,12 +604,46 @@ __device__ __forceinline__ void render_group(const ObsOut& o, ObsLds<HW, M>& L, 
 // and stores its entry; USE loads the 16-B entry instead of the two rows and skips the decode,
 // unless some acting env of the wave has an untagged entry or actions off the regular path:
 // that wave then loads its rows (a second round trip) and decodes them as without a cache.
-template <int HW, class M, int LPE, bool kFin, bool kFirst, bool kLate, bool kBoards, class Ix, class AtEnd>
-__device__ __forceinline__ void turn_env(const rmi_sokoban_t& env, const rmi_episode_t& ep, const rmi_turn_t& in,
-                                         int hw_rt, uint64_t border, uint8_t* __restrict__ err_out,
-                                         const rmi_finalize_t& fin, const uint8_t* __restrict__ init_state,
-                                         const int8_t* __restrict__ init_player, int64_t b, int sub, uint32_t* ls,
-                                         uint32_t* lf, AtEnd&& at_end) {
+template <int HW, class M, int LPE, bool kFin, bool kFirst, bool kLate, bool kBoards, class Ix, bool kPin = true,
+          class AtEnd>
+__device__ __forceinline__ void turn_env(const rmi_sokoban_t& env_arg, const rmi_episode_t& ep_arg,
+                                         const rmi_turn_t& in_arg, int hw_rt, uint32_t w_magic, uint64_t border,
+                                         uint8_t* err_out, const rmi_finalize_t& fin_arg, const uint8_t* init_state,
+                                         const int8_t* init_player, int64_t b, int sub, uint32_t* ls, uint32_t* lf,
+                                         AtEnd&& at_end) {
+  RMI_STAMP_DECL;
+  RMI_STAMP(0);
+  // ---- 0. the kernel arguments the turn's regular path reads, all fetched here in one batch of
+  //         scalar loads behind one wait, ahead of the first vector load (args_pin, common.hpp).
+  //         Left to itself the compiler sinks each argument's load to its first use and waits
+  //         there: for K before the action loads, for the action cap before the step block, for
+  //         format_penalty / err_out (a scalar-cache line nothing earlier touched) in front of
+  //         every output store.  What only the decode or the exact path reads (border, H, and
+  //         under the board cache room_fixed) is not fetched ahead.  The struct copies keep the
+  //         pinned values: everything below reads them, not the arguments.  (kPin = false: the
+  //         token turn, which runs this after its decode and parse at a 64-VGPR budget, where
+  //         arguments held from here on only add spills.)
+  rmi_sokoban_t env = env_arg;
+  rmi_episode_t ep = ep_arg;
+  rmi_turn_t in = in_arg;
+  const rmi_finalize_t& fin = fin_arg;
+  if constexpr (kPin) {
+    args_pin(ep.B, env.W, env.num_boxes, env.max_steps, env.room_state, env.player, env.num_env_steps,
+             env.boxes_on_target, ep.num_actions, ep.flags, ep.n_turns, ep.penalty, ep.turn_reward, ep.turn_info,
+             ep.turn_exec, in.turn, in.K, in.actions, in.n_actions, in.has_input, in.max_actions_per_traj,
+             in.format_penalty, err_out, w_magic);
+    if (kBoards) args_pin(env.boards, env.boards_mode);
+    if (!kBoards) args_pin(env.room_fixed, env.H, border);
+    if (!HW) args_pin(hw_rt);
+    if (kFirst) args_pin(init_state, init_player, ep.T);
+    if (kFirst && kBoards) args_pin(env.room_fixed, env.init_boards);
+    // (kFin: the finalize's own arguments are left to the compiler, which fetches them at the
+    // finalize, after the turn's stores are issued -- a scalar-cache hit, they share their 64-B line
+    // with w_magic and err_out above.  Pinned here they cost the last turn 30 spilled SGPRs, and the
+    // rollout 0.3 us: DESIGN §3.1.)
+    if (kFin && !kFirst) args_pin(ep.T);
+  }
+
   constexpr int NW = HW ? HW / 4 : kMaxWords;
   constexpr int NWL = (NW + LPE - 1) / LPE;      // row dwords per lane
   const int hw = HW ? HW : hw_rt;
@@ -617,7 +651,6 @@ __device__ __forceinline__ void turn_env(const rmi_sokoban_t& env, const rmi_epi
   const int B = ep.B;
   const bool live = b < B;
   const int H = env.H, W = env.W;
-  const uint32_t w_magic = (65536u + (uint32_t)W - 1u) / (uint32_t)W;  // off the critical path
   static_assert(!kBoards || (HW == 36 && LPE == 1 && !kLate && sizeof(M) == 4), "the board cache: 6x6, u32 window");
   // the cache mode of this launch (wave-uniform).  A fresh episode's first turn (kFirst) reads
   // the RESET state: under USE from env.init_boards (the reset rows' entries, written by a
@@ -625,8 +658,6 @@ __device__ __forceinline__ void turn_env(const rmi_sokoban_t& env, const rmi_epi
   const int bmode = kBoards && env.boards ? (kFirst && !env.init_boards ? RMI_BOARDS_BUILD : env.boards_mode)
                                           : RMI_BOARDS_NONE;
   const bool use = bmode == RMI_BOARDS_USE;
-  RMI_STAMP_DECL;
-  RMI_STAMP(0);
 
   // ---- 1. every load of the turn, issued together: branch-free from clamped (always valid)
   //         addresses, rows first, nothing consumed before the last load is issued — so the
@@ -957,7 +988,7 @@ __device__ __forceinline__ void turn_env(const rmi_sokoban_t& env, const rmi_epi
 template <int HW, class M, int LPE, bool kFin, bool kFirst = false, bool kLate = false, bool kObs = false,
           class Ix = int64_t>  // HW = H*W (0 = runtime); H*W % 4 == 0
 __global__ __launch_bounds__(kWave * kSokWpb * (kObs ? kObsFan : 1)) void sokoban_step_turn_kernel(rmi_sokoban_t env, rmi_episode_t ep, rmi_turn_t in,
-                                                                  int hw_rt, uint64_t border,
+                                                                  int hw_rt, uint32_t w_magic, uint64_t border,
                                                                   uint8_t* __restrict__ err_out, rmi_finalize_t fin,
                                                                   const uint8_t* __restrict__ init_state = nullptr,
                                                                   const int8_t* __restrict__ init_player = nullptr,
@@ -999,7 +1030,7 @@ __global__ __launch_bounds__(kWave * kSokWpb * (kObs ? kObsFan : 1)) void sokoba
       };
   constexpr bool kBoards = HW == 36 && LPE == 1 && !kLate && !kObs && sizeof(M) == 4;
   static_assert(sizeof(Ix) == 8 || kBoards, "32-bit env offsets: the SK layout only (launched below kOff32MaxB envs)");
-  turn_env<HW, M, LPE, kFin, kFirst, kLate, kBoards, Ix>(env, ep, in, hw_rt, border, err_out, fin, init_state,
+  turn_env<HW, M, LPE, kFin, kFirst, kLate, kBoards, Ix>(env, ep, in, hw_rt, w_magic, border, err_out, fin, init_state,
                                                          init_player, b, sub, lds_state + (wave * kEnvs + slot) * row_words,
                                                          lds_fixed + (wave * kEnvs + slot) * row_words, at_end);
 }
@@ -1118,7 +1149,7 @@ __host__ __device__ constexpr size_t tok_static_lds() {
 
 template <bool kFin, bool kFirst>
 __global__ __launch_bounds__(kWave* kTokEnvs) __attribute__((amdgpu_waves_per_eu(8))) void sokoban_token_turn_kernel(
-    DetokArgs d, ParseArgs a, rmi_sokoban_t env, rmi_episode_t ep, rmi_turn_t in, uint64_t border,
+    DetokArgs d, ParseArgs a, rmi_sokoban_t env, rmi_episode_t ep, rmi_turn_t in, uint32_t w_magic, uint64_t border,
     uint8_t* __restrict__ err_out, rmi_finalize_t fin, const uint8_t* __restrict__ init_state,
     const int8_t* __restrict__ init_player, ObsOut obs, const uint8_t* __restrict__ has_t, uint8_t* __restrict__ has) {
   extern __shared__ uint64_t lds_q[];  // kTokEnvs parse regions (parse_lds(stride) each)
@@ -1183,8 +1214,8 @@ __global__ __launch_bounds__(kWave* kTokEnvs) __attribute__((amdgpu_waves_per_eu
   if (wv < kTurnWaves) {
     const int t = wv * kWave + lane, e = t / kLpeT, sub = t % kLpeT;
     const int64_t be = b0 + e;
-    turn_env<36, uint32_t, kLpeT, false, kFirst, false, false, int64_t>(
-        env, ep, in, 36, border, err_out, fin, init_state, init_player, be, sub, lds_state + e * 9, lds_fixed + e * 9,
+    turn_env<36, uint32_t, kLpeT, false, kFirst, false, false, int64_t, false>(
+        env, ep, in, 36, w_magic, border, err_out, fin, init_state, init_player, be, sub, lds_state + e * 9, lds_fixed + e * 9,
         [&](const auto& xs, const auto& xf, uint32_t wall, uint32_t target, uint32_t box, int jp) {
 #pragma unroll
           for (int i = 0; i < (9 + kLpeT - 1) / kLpeT; ++i) {
@@ -1273,6 +1304,10 @@ __global__ __launch_bounds__(kWave* kTokEnvs) __attribute__((amdgpu_waves_per_eu
 #endif
 namespace rmi {
 namespace {
+// p / W == (p * w_magic(W)) >> 16 for p < 2^10, W < 2^10: host arithmetic on the struct, so the
+// launcher passes it instead of every wave dividing
+inline uint32_t w_magic_of(int W) { return (65536u + (uint32_t)W - 1u) / (uint32_t)W; }
+
 template <bool kFin, bool kFirst = false>
 int sokoban_step_turn_launch(const rmi_sokoban_t* env, const rmi_episode_t* ep, const rmi_turn_t* in, uint8_t* err,
                              const rmi_finalize_t& fin, hipStream_t s, const uint8_t* init_state = nullptr,
@@ -1285,6 +1320,7 @@ int sokoban_step_turn_launch(const rmi_sokoban_t* env, const rmi_episode_t* ep, 
     for (int c = 0; c < W; ++c)
       if (r == 0 || c == 0 || r == H - 1 || c == W - 1) border |= 1ull << (r * W + c);
   const bool w32 = (H - 1) * W <= 32;  // the board window fits a u32
+  const uint32_t w_magic = w_magic_of(W);
   // lanes per env: spread a batch too small to fill the chip over 4 lanes per env
   const bool spread = spread_lanes(ep->B);
   const bool late = !kFirst && !spread && ep->B >= RMI_SOK_LATE_MIN;
@@ -1299,24 +1335,24 @@ int sokoban_step_turn_launch(const rmi_sokoban_t* env, const rmi_episode_t* ep, 
       hipLaunchKernelGGL((sokoban_step_turn_kernel<HW_, M_, kSpreadLpe, kFin, kFirst>),                       \
                          dim3((unsigned)((ep->B + kWave * kSokWpb / kSpreadLpe - 1) /                          \
                                          (kWave * kSokWpb / kSpreadLpe))),                                   \
-                         dim3(kWave * kSokWpb), 0, s, *env, *ep, *in, hw, border, err, fin, init_state,      \
+                         dim3(kWave * kSokWpb), 0, s, *env, *ep, *in, hw, w_magic, border, err, fin, init_state, \
                          init_player);                                                                        \
     else if (late) {                                                                                          \
       if constexpr (!kFirst)                                                                                  \
         hipLaunchKernelGGL((sokoban_step_turn_kernel<HW_, M_, 1, kFin, false, true>), dim3(grid),            \
-                           dim3(kWave * kSokWpb), 0, s, *env, *ep, *in, hw, border, err, fin, init_state,    \
+                           dim3(kWave * kSokWpb), 0, s, *env, *ep, *in, hw, w_magic, border, err, fin, init_state, \
                            init_player);                                                                      \
     } else {                                                                                                  \
       if constexpr (HW_ == 36 && sizeof(M_) == 4) {                                                           \
         if (ep->B < kOff32MaxB) {                                                                             \
           hipLaunchKernelGGL((sokoban_step_turn_kernel<HW_, M_, 1, kFin, kFirst, false, false, uint32_t>),    \
-                             dim3(grid), dim3(kWave * kSokWpb), 0, s, *env, *ep, *in, hw, border, err, fin,   \
+                             dim3(grid), dim3(kWave * kSokWpb), 0, s, *env, *ep, *in, hw, w_magic, border, err, fin, \
                              init_state, init_player);                                                        \
           break;                                                                                              \
         }                                                                                                     \
       }                                                                                                       \
       hipLaunchKernelGGL((sokoban_step_turn_kernel<HW_, M_, 1, kFin, kFirst>), dim3(grid), dim3(kWave * kSokWpb), \
-                         0, s, *env, *ep, *in, hw, border, err, fin, init_state, init_player);                \
+                         0, s, *env, *ep, *in, hw, w_magic, border, err, fin, init_state, init_player);        \
     }                                                                                                         \
   } while (0)
   // (the SK layout -- 6x6 u32 window, one lane per env, early row loads -- addresses the env
@@ -1350,13 +1386,14 @@ int sokoban_step_turn_obs_launch(const rmi_sokoban_t* env, const rmi_episode_t* 
     for (int c = 0; c < W; ++c)
       if (r == 0 || c == 0 || r == H - 1 || c == W - 1) border |= 1ull << (r * W + c);
   const bool w32 = (H - 1) * W <= 32;
+  const uint32_t w_magic = w_magic_of(W);
   const dim3 grid((unsigned)((ep->B + kWave * kSokWpb - 1) / (kWave * kSokWpb))), block(kWave * kSokWpb * kObsFan);
   if (w32)
     hipLaunchKernelGGL((sokoban_step_turn_kernel<36, uint32_t, 1, kFin, kFirst, false, true>), grid, block, 0, s, *env,
-                       *ep, *in, hw, border, err, fin, init_state, init_player, obs);
+                       *ep, *in, hw, w_magic, border, err, fin, init_state, init_player, obs);
   else
     hipLaunchKernelGGL((sokoban_step_turn_kernel<36, uint64_t, 1, kFin, kFirst, false, true>), grid, block, 0, s, *env,
-                       *ep, *in, hw, border, err, fin, init_state, init_player, obs);
+                       *ep, *in, hw, w_magic, border, err, fin, init_state, init_player, obs);
   return launch_status();
 }
 
@@ -1581,13 +1618,13 @@ RMI_API int rmi_sokoban_token_turn(const rmi_token_rows_t* tok, const rmi_sokoba
   const dim3 grid((unsigned)((B + kTokEnvs - 1) / kTokEnvs)), block(kWave * kTokEnvs);
   hipStream_t s = as_stream(stream);
   if (fin)
-    hipLaunchKernelGGL((sokoban_token_turn_kernel<true, false>), grid, block, shm, s, d, a, *env, *ep, *in, border, err, f,
+    hipLaunchKernelGGL((sokoban_token_turn_kernel<true, false>), grid, block, shm, s, d, a, *env, *ep, *in, w_magic_of(W), border, err, f,
                        nullptr, nullptr, o, tok->has_t, tok->has);
   else if (init_state)
-    hipLaunchKernelGGL((sokoban_token_turn_kernel<false, true>), grid, block, shm, s, d, a, *env, *ep, *in, border, err, f,
+    hipLaunchKernelGGL((sokoban_token_turn_kernel<false, true>), grid, block, shm, s, d, a, *env, *ep, *in, w_magic_of(W), border, err, f,
                        init_state, init_player, o, tok->has_t, tok->has);
   else
-    hipLaunchKernelGGL((sokoban_token_turn_kernel<false, false>), grid, block, shm, s, d, a, *env, *ep, *in, border, err,
+    hipLaunchKernelGGL((sokoban_token_turn_kernel<false, false>), grid, block, shm, s, d, a, *env, *ep, *in, w_magic_of(W), border, err,
                        f, nullptr, nullptr, o, tok->has_t, tok->has);
   return launch_status();
 }
