@@ -445,6 +445,46 @@ int rmi_rloo_outcome(const float* r, const uint8_t* mask, int64_t B, int64_t L, 
  * REINFORCE++-baseline estimators (agent_trainer.py:102-117) after their masked_whiten. */
 int rmi_mask_mul(float* x, const uint8_t* mask, int64_t n, rmi_stream_t stream);
 
+/* Replaces: verl apply_kl_penalty / core_algos.kl_penalty (called agent_trainer.py:613-615):
+ * rewards = scores - (float)beta * kld with kld = estimator(old_log_probs, ref_log_prob) *
+ * (float)(mask != 0), every step an f32 operation in the reference's order; kind 0 kl
+ * (old - ref), 1 abs, 2 mse (0.5 * d * d), 3 low_var_kl (clamp(exp(k) - k - 1, -10, 10),
+ * k = ref - old).  mask u8[B,L]: loss_mask[:, -L:] (multi_turn) or attention_mask[:, -L:].
+ * row_stats f64[B,2] = (sum_t kld, sum_t mask) per row, summed in fp64 in an order fixed by
+ * the column alone (the same bits for a row wherever it lies).  A non-finite log-prob under a
+ * zero mask gives NaN (the mask is a multiply), as in torch.                                   */
+int rmi_kl_reward(const float* scores, const float* old_log_probs, const float* ref_log_prob, const uint8_t* mask,
+                  int64_t B, int64_t L, double beta, int32_t kind, float* rewards, double* row_stats,
+                  rmi_stream_t stream);
+
+/* out[0] = mean over i < n of x[i*stride] (den NULL) or x[i*stride] / den[i*stride], in fp64
+ * and in an order that depends on n only: apply_kl_penalty's current_kl from row_stats
+ * (x = row_stats, den = row_stats + 1, stride 2), the same bits for a whole batch and for its
+ * gathered shards.  A row with mask sum 0 is 0/0 = NaN, as verl's masked_mean(axis=-1).
+ * n == 0 leaves out untouched.                                                                */
+int rmi_rows_mean(const double* x, const double* den, int64_t n, int64_t stride, double* out, rmi_stream_t stream);
+
+/* Replaces: grpo_advantage_length_weight's relative lengths (agent_trainer.py:637-639).
+ * rmi_length_weight_rows: count[b] = nonzero bytes of row b of mask u8[B,L]; with rel (optional)
+ * also the finalize step over these B rows.  rmi_length_weight_finalize: rel[i] =
+ * ((float)count[i] + 1e-6f) / mean with mean = (float)(exact integer sum of count) / (float)n
+ * — separate so a sharded batch can feed it every rank's gathered counts.                     */
+int rmi_length_weight_rows(const uint8_t* mask, int64_t B, int64_t L, int32_t* count, float* rel,
+                           rmi_stream_t stream);
+int rmi_length_weight_finalize(const int32_t* count, int64_t n, float* rel, rmi_stream_t stream);
+
+/* rmi_grpo_outcome with the length weight fused (agent_trainer.py:94-99 then :636-641): the
+ * advantage's row score is divided by row_scale[row] before the broadcast over the mask,
+ * bit-equal to (adv * mask) / rel; ret stays unweighted (the reference overwrites only
+ * advantages).  row_scale NULL = rmi_grpo_outcome.                                            */
+int rmi_grpo_outcome_scaled(const float* r, const uint8_t* mask, int64_t B, int64_t L, const int32_t* seg, int32_t G,
+                            double eps, int32_t norm_by_std, const float* row_scale, float* adv, float* ret,
+                            rmi_stream_t stream);
+
+/* x[b, :] /= scale[b] in place (f32 division): agent_trainer.py:640 for callers that keep the
+ * reference's order, compute_advantage first and the weighting after.                         */
+int rmi_row_div(float* x, const float* scale, int64_t B, int64_t L, rmi_stream_t stream);
+
 /* ------------------------------------------------ response -> action ids (§8(f) rank 2)
  * Replaces: ContextManager.get_env_inputs (ctx_manager.py:332-352): the tokenizer's
  *           batch_decode(responses, skip_special_tokens=True) (:334-337), the "<think>" /

@@ -226,6 +226,14 @@ _SIGS = {
     "rmi_rloo_outcome": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p,
                                    c_void_p]),
     "rmi_mask_mul": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "rmi_kl_reward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_double, c_int32, c_void_p,
+                                c_void_p, c_void_p]),
+    "rmi_rows_mean": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "rmi_length_weight_rows": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "rmi_length_weight_finalize": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "rmi_grpo_outcome_scaled": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_double, c_int32,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rmi_row_div": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "rmi_detokenize": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                  c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "rmi_vocab_pack": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),

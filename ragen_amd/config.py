@@ -1,7 +1,7 @@
 """Config objects with OmegaConf-like attribute access (hydra/omegaconf are absent offline).
 
 ``default_config()`` holds the hot-path keys of config/base.yaml and config/envs.yaml
-(base.yaml:75-124, envs.yaml:1-148) with the same names and default values; task
+(base.yaml:12, 75-124, envs.yaml:1-148) with the same names and default values; task
 overrides (``_2_sokoban`` etc.) are plain nested dict updates.  YAML files with the same
 structure load through ``load_config``.
 """
@@ -39,10 +39,12 @@ _SOKOBAN_INSTR = ("You are solving the Sokoban puzzle. You are the player and yo
 DEFAULTS = {
     "model_path": "Qwen/Qwen2.5-0.5B-Instruct",
     "enable_response_mask": True,
+    "grpo_advantage_length_weight": False,
     "actor_rollout_ref": {"rollout": {"response_length": 400, "rollout_filter_ratio": 0.25,
                                       "rollout_filter_type": "std", "n": 1}},
     "algorithm": {"gamma": 1.0, "lam": 1.0, "high_level_gamma": 0.95, "adv_estimator": "gae",
-                  "bi_level_gae": False, "norm_adv_by_std_in_grpo": True},
+                  "bi_level_gae": False, "norm_adv_by_std_in_grpo": True, "use_kl_in_reward": False,
+                  "kl_penalty": "kl", "kl_ctrl": {"type": "fixed", "kl_coef": 0.0}},
     "agent_proxy": {"max_context_window": -1, "max_turn": 5, "action_sep": "||", "max_actions_per_turn": 5,
                     "use_turn_scores": False, "enable_think": True,
                     "reward_normalization": {"grouping": "state", "method": "identity"}},

@@ -9,6 +9,7 @@
 //                    whitening (agent_trainer.py:110-117)
 //  rmi_remax         verl compute_remax_outcome_advantage (agent_trainer.py:118-126)
 //  rmi_rloo_outcome  verl compute_rloo_outcome_advantage (agent_trainer.py:127-134)
+//  rmi_grpo_outcome_scaled  rmi_grpo_outcome with grpo_advantage_length_weight (agent_trainer.py:636-641)
 //  rmi_mask_mul      the trailing `* response_mask` of verl's REINFORCE++ estimators
 //
 // Exactness: the GAE recurrence runs sequentially per row in the reference's f32 op order
@@ -1186,6 +1187,9 @@ __global__ __launch_bounds__(kBlock) void mask_mul_kernel(float* __restrict__ x,
 // boundaries of the flat index (a head and a tail of < 4 elements, one per lane, and a body
 // where a lane moves 4 columns with 16-B accesses), whatever L is; `vec` = the base pointers
 // allow it.
+// SCALED (rmi_grpo_outcome_scaled, grpo_advantage_length_weight, agent_trainer.py:636-641): the
+// advantage's row score is divided by row_scale[row] before the broadcast — (sc / rel) * mask is
+// the reference's (sc * mask) / rel bit for bit, the sign of a zero included; ret keeps sc.
 struct GrpoSpan {
   int64_t o, b0, b1, e;  // row start, body [b0, b1) (multiples of 4), row end
 };
@@ -1206,10 +1210,12 @@ __device__ __forceinline__ double grpo_row_sum(const float* __restrict__ r, cons
   return wave_sum(s);
 }
 
+template <bool SCALED = false>
 __global__ __launch_bounds__(kBlock) void grpo_kernel(const float* __restrict__ r, const uint8_t* __restrict__ mask,
                                                       int64_t B, int64_t L, const int32_t* __restrict__ seg, int G,
                                                       float eps, int norm_by_std, float* __restrict__ adv,
-                                                      float* __restrict__ ret) {
+                                                      float* __restrict__ ret,
+                                                      const float* __restrict__ row_scale = nullptr) {
   const int lane = threadIdx.x & 63;
   const int g = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
   if (g >= G) return;
@@ -1245,22 +1251,43 @@ __global__ __launch_bounds__(kBlock) void grpo_kernel(const float* __restrict__ 
       sc = sf - mean;
       if (norm_by_std) sc = sc / (sd + eps);
     }
-    for (int64_t i = sp.o + lane; i < sp.b0; i += 64) {
-      const float y = sc * (float)(mask[i] != 0);
-      adv[i] = y;
-      ret[i] = y;
-    }
-    for (int64_t i = sp.b0 + 4 * lane; i < sp.b1; i += 256) {
-      const uint32_t m4 = *reinterpret_cast<const uint32_t*>(mask + i);
-      const float4 y = make_float4(sc * (float)((m4 & 0xFFu) != 0), sc * (float)((m4 & 0xFF00u) != 0),
-                                   sc * (float)((m4 & 0xFF0000u) != 0), sc * (float)((m4 >> 24) != 0));
-      *reinterpret_cast<float4*>(adv + i) = y;
-      *reinterpret_cast<float4*>(ret + i) = y;
-    }
-    for (int64_t i = sp.b1 + lane; i < sp.e; i += 64) {
-      const float y = sc * (float)(mask[i] != 0);
-      adv[i] = y;
-      ret[i] = y;
+    if constexpr (!SCALED) {
+      for (int64_t i = sp.o + lane; i < sp.b0; i += 64) {
+        const float y = sc * (float)(mask[i] != 0);
+        adv[i] = y;
+        ret[i] = y;
+      }
+      for (int64_t i = sp.b0 + 4 * lane; i < sp.b1; i += 256) {
+        const uint32_t m4 = *reinterpret_cast<const uint32_t*>(mask + i);
+        const float4 y = make_float4(sc * (float)((m4 & 0xFFu) != 0), sc * (float)((m4 & 0xFF00u) != 0),
+                                     sc * (float)((m4 & 0xFF0000u) != 0), sc * (float)((m4 >> 24) != 0));
+        *reinterpret_cast<float4*>(adv + i) = y;
+        *reinterpret_cast<float4*>(ret + i) = y;
+      }
+      for (int64_t i = sp.b1 + lane; i < sp.e; i += 64) {
+        const float y = sc * (float)(mask[i] != 0);
+        adv[i] = y;
+        ret[i] = y;
+      }
+    } else {
+      const float sa = __fdiv_rn(sc, row_scale[row]);  // the advantage's score; ret keeps sc
+      for (int64_t i = sp.o + lane; i < sp.b0; i += 64) {
+        const float m = (float)(mask[i] != 0);
+        adv[i] = sa * m;
+        ret[i] = sc * m;
+      }
+      for (int64_t i = sp.b0 + 4 * lane; i < sp.b1; i += 256) {
+        const uint32_t m4 = *reinterpret_cast<const uint32_t*>(mask + i);
+        const float m0 = (float)((m4 & 0xFFu) != 0), m1 = (float)((m4 & 0xFF00u) != 0),
+                    m2 = (float)((m4 & 0xFF0000u) != 0), m3 = (float)((m4 >> 24) != 0);
+        *reinterpret_cast<float4*>(adv + i) = make_float4(sa * m0, sa * m1, sa * m2, sa * m3);
+        *reinterpret_cast<float4*>(ret + i) = make_float4(sc * m0, sc * m1, sc * m2, sc * m3);
+      }
+      for (int64_t i = sp.b1 + lane; i < sp.e; i += 64) {
+        const float m = (float)(mask[i] != 0);
+        adv[i] = sa * m;
+        ret[i] = sc * m;
+      }
     }
   }
 }
@@ -1404,8 +1431,21 @@ RMI_API int rmi_grpo_outcome(const float* r, const uint8_t* mask, int64_t B, int
   if (!r || !mask || !seg || !adv || !ret || B < 0 || L < 0 || G < 0) return RMI_EINVAL;
   if (B == 0 || G == 0) return RMI_OK;
   const int per = kBlock / 64;
-  hipLaunchKernelGGL(grpo_kernel, dim3((G + per - 1) / per), dim3(kBlock), 0, as_stream(stream), r, mask, B, L, seg, G,
+  hipLaunchKernelGGL(grpo_kernel<false>, dim3((G + per - 1) / per), dim3(kBlock), 0, as_stream(stream), r, mask, B, L, seg, G,
                      (float)eps, norm_by_std, adv, ret);
+  return launch_status();
+}
+
+RMI_API int rmi_grpo_outcome_scaled(const float* r, const uint8_t* mask, int64_t B, int64_t L, const int32_t* seg,
+                                    int32_t G, double eps, int32_t norm_by_std, const float* row_scale, float* adv,
+                                    float* ret, rmi_stream_t stream) {
+  using namespace rmi;
+  if (!row_scale) return rmi_grpo_outcome(r, mask, B, L, seg, G, eps, norm_by_std, adv, ret, stream);
+  if (!r || !mask || !seg || !adv || !ret || B < 0 || L < 0 || G < 0) return RMI_EINVAL;
+  if (B == 0 || G == 0) return RMI_OK;
+  const int per = kBlock / 64;
+  hipLaunchKernelGGL(grpo_kernel<true>, dim3((G + per - 1) / per), dim3(kBlock), 0, as_stream(stream), r, mask, B, L,
+                     seg, G, (float)eps, norm_by_std, adv, ret, row_scale);
   return launch_status();
 }
 
@@ -1438,7 +1478,7 @@ RMI_API int rmi_rloo_outcome(const float* r, const uint8_t* mask, int64_t B, int
   if (!r || !mask || !seg || !adv || !ret || B < 0 || L < 0 || G < 0) return RMI_EINVAL;
   if (B == 0 || G == 0) return RMI_OK;
   const int per = kBlock / 64;
-  hipLaunchKernelGGL(grpo_kernel, dim3((G + per - 1) / per), dim3(kBlock), 0, as_stream(stream), r, mask, B, L, seg, G,
+  hipLaunchKernelGGL(grpo_kernel<false>, dim3((G + per - 1) / per), dim3(kBlock), 0, as_stream(stream), r, mask, B, L, seg, G,
                      0.0f, 2, adv, ret);
   return launch_status();
 }

@@ -103,6 +103,16 @@ def global_whiten_stats(row_stats: torch.Tensor, group=None, sizes=None) -> torc
     return all_gather_rows(row_stats, group=group, sizes=sizes)
 
 
+def gather_row_values(values: torch.Tensor, group=None, sizes=None, with_offset: bool = False):
+    """Per-row values of this rank's shard [n_local, ...] -> every rank's, in global row order:
+    apply_kl_penalty's per-row f64 (sum kld, sum mask) and the length weight's i32 row counts.
+    Each is then reduced by the same kernel as a whole batch's (rows_mean /
+    length_weight_finalize), so every rank gets the 1-GPU run's bits.  With ``sizes`` (every
+    rank's row count) free of host synchronisation; with_offset: -> (values, this rank's first
+    row among them)."""
+    return all_gather_rows(values, with_offset=with_offset, group=group, sizes=sizes)
+
+
 def gather_group_scores(scores: torch.Tensor, group_size: int, with_offset: bool = False, group=None):
     """Per-env trajectory scores of the local groups -> all groups' scores (global order);
     with_offset also returns the first global GROUP index of this rank."""

@@ -1409,3 +1409,102 @@ def grpo_outcome(r, mask, seg, eps=1e-6, norm_by_std=True):
     check(lib().rmi_grpo_outcome(_ptr(r), _ptr(m), B, L, _ptr(seg), seg.numel() - 1, float(eps), int(norm_by_std),
                                  _ptr(adv), _ptr(ret), _stream(r.device)), "rmi_grpo_outcome")
     return adv, ret
+
+
+def grpo_outcome_scaled(r, mask, seg, eps=1e-6, norm_by_std=True, row_scale=None):
+    """grpo_outcome with grpo_advantage_length_weight fused (agent_trainer.py:636-641): adv's row
+    score is divided by row_scale f32[B] (the relative lengths) before the broadcast; ret stays
+    unweighted.  row_scale=None is grpo_outcome."""
+    _dev(r, mask, row_scale)
+    _dt(r, torch.float32, "token_level_rewards")
+    _dt(row_scale, torch.float32, "row_scale")
+    B, L = _rows(r, mask, names=("response_mask",))
+    if row_scale is not None and (row_scale.dim() != 1 or row_scale.shape[0] != B or not row_scale.is_contiguous()):
+        raise ValueError(f"row_scale must be a contiguous f32[{B}]")
+    seg = segments(seg, B, r.device)
+    if seg.device != r.device:
+        raise ValueError("seg must be on the rows' device")
+    m = _mask_u8(mask).contiguous()
+    adv = torch.empty_like(r)
+    ret = torch.empty_like(r)
+    check(lib().rmi_grpo_outcome_scaled(_ptr(r), _ptr(m), B, L, _ptr(seg), seg.numel() - 1, float(eps),
+                                        int(norm_by_std), _ptr(row_scale), _ptr(adv), _ptr(ret), _stream(r.device)),
+          "rmi_grpo_outcome_scaled")
+    return adv, ret
+
+
+# ------------------------------------------------- KL in reward, GRPO length weight
+KL_KINDS = {"kl": 0, "abs": 1, "mse": 2, "low_var_kl": 3}
+
+
+def kl_reward(scores, old_log_probs, ref_log_prob, mask, beta, kind="kl"):
+    """verl apply_kl_penalty's tensor part (agent_trainer.py:613-615): -> (token_level_rewards
+    f32[B, L], row_stats f64[B, 2] = per-row (sum kld * mask, sum mask))."""
+    if kind not in KL_KINDS:
+        raise NotImplementedError(f"kl_penalty {kind!r}")
+    _dev(scores, old_log_probs, ref_log_prob, mask)
+    for t, nm in ((scores, "token_level_scores"), (old_log_probs, "old_log_probs"), (ref_log_prob, "ref_log_prob")):
+        _dt(t, torch.float32, nm)
+        if not t.is_contiguous():
+            raise ValueError(f"{nm} must be contiguous")
+    B, L = _rows(scores, old_log_probs, ref_log_prob, mask, names=("old_log_probs", "ref_log_prob", "mask"))
+    m = _mask_u8(mask).contiguous()
+    rewards = torch.empty_like(scores)
+    row_stats = torch.empty(B, 2, dtype=torch.float64, device=scores.device)
+    check(lib().rmi_kl_reward(_ptr(scores), _ptr(old_log_probs), _ptr(ref_log_prob), _ptr(m), B, L, float(beta),
+                              KL_KINDS[kind], _ptr(rewards), _ptr(row_stats), _stream(scores.device)), "rmi_kl_reward")
+    return rewards, row_stats
+
+
+def rows_mean(x):
+    """f64[1] = the mean of x f64[n], or of row_stats[:, 0] / row_stats[:, 1] for x f64[n, 2]
+    (kl_reward's row_stats -> current_kl), in an order fixed by n; NaN for n == 0."""
+    _dev(x)
+    _dt(x, torch.float64, "x")
+    if x.dim() not in (1, 2) or (x.dim() == 2 and x.shape[1] != 2) or not x.is_contiguous():
+        raise ValueError(f"rows_mean takes a contiguous f64[n] or f64[n, 2], got {tuple(x.shape)}")
+    out = torch.full((1,), float("nan"), dtype=torch.float64, device=x.device)
+    ratio = x.dim() == 2
+    den = x.data_ptr() + 8 if ratio else None
+    check(lib().rmi_rows_mean(_ptr(x), den, x.shape[0], 2 if ratio else 1, _ptr(out), _stream(x.device)),
+          "rmi_rows_mean")
+    return out
+
+
+def length_weight_rows(mask):
+    """grpo_advantage_length_weight's row statistics (agent_trainer.py:637-639) of a [B, L] mask:
+    -> (count i32[B], rel f32[B] = (count + 1e-6) / mean(count))."""
+    _dev(mask)
+    if mask.dim() != 2:
+        raise ValueError(f"expected a [B, L] mask, got shape {tuple(mask.shape)}")
+    m = _mask_u8(mask).contiguous()
+    B, L = m.shape
+    count = torch.empty(B, dtype=torch.int32, device=m.device)
+    rel = torch.empty(B, dtype=torch.float32, device=m.device)
+    check(lib().rmi_length_weight_rows(_ptr(m), B, L, _ptr(count), _ptr(rel), _stream(m.device)),
+          "rmi_length_weight_rows")
+    return count, rel
+
+
+def length_weight_finalize(count):
+    """rel f32[n] from count i32[n] (every shard's counts in global row order)."""
+    _dev(count)
+    _dt(count, torch.int32, "count")
+    if count.dim() != 1 or not count.is_contiguous():
+        raise ValueError("count must be a contiguous i32[n]")
+    rel = torch.empty(count.shape[0], dtype=torch.float32, device=count.device)
+    check(lib().rmi_length_weight_finalize(_ptr(count), count.shape[0], _ptr(rel), _stream(count.device)),
+          "rmi_length_weight_finalize")
+    return rel
+
+
+def row_div_(x, scale):
+    """x[b, :] /= scale[b] in place (f32): agent_trainer.py:640."""
+    _dev(x, scale)
+    _dt(x, torch.float32, "advantages")
+    _dt(scale, torch.float32, "scale")
+    if x.dim() != 2 or not x.is_contiguous() or scale.dim() != 1 or scale.shape[0] != x.shape[0] \
+            or not scale.is_contiguous():
+        raise ValueError("row_div_: x contiguous f32[B, L], scale contiguous f32[B]")
+    check(lib().rmi_row_div(_ptr(x), _ptr(scale), x.shape[0], x.shape[1], _stream(x.device)), "rmi_row_div")
+    return x

@@ -586,6 +586,80 @@ def _(x, mask):
     return None
 
 
+# ============================= KL in reward, GRPO length weight (agent_trainer.py:612-641)
+KL_KIND_NAMES = tuple(ops.KL_KINDS)  # kind 0 kl, 1 abs, 2 mse, 3 low_var_kl
+
+
+@_op("kl_reward")
+def kl_reward(scores: Tensor, old_log_probs: Tensor, ref_log_prob: Tensor, mask: Tensor, beta: float,
+              kind: int) -> Tuple[Tensor, Tensor]:
+    """verl apply_kl_penalty's tensor part -> (token_level_rewards, row_stats f64[B, 2])."""
+    if not 0 <= kind < len(KL_KIND_NAMES):
+        raise ValueError(f"kl_reward kind must be 0..3, got {kind}")
+    return ops.kl_reward(scores, old_log_probs, ref_log_prob, mask, beta, KL_KIND_NAMES[kind])
+
+
+@kl_reward.register_fake
+def _(scores, old_log_probs, ref_log_prob, mask, beta, kind):
+    return torch.empty_like(scores), scores.new_empty(scores.shape[0], 2, dtype=torch.float64)
+
+
+@_op("rows_mean")
+def rows_mean(x: Tensor) -> Tensor:
+    """f64[1]: mean of x f64[n], or of x[:, 0] / x[:, 1] for f64[n, 2] (current_kl), fixed order."""
+    return ops.rows_mean(x)
+
+
+@rows_mean.register_fake
+def _(x):
+    return x.new_empty(1, dtype=torch.float64)
+
+
+@_op("length_weight_rows")
+def length_weight_rows(mask: Tensor) -> Tuple[Tensor, Tensor]:
+    """-> (count i32[B], rel f32[B] = (count + 1e-6) / mean(count)) of a [B, L] mask."""
+    return ops.length_weight_rows(mask)
+
+
+@length_weight_rows.register_fake
+def _(mask):
+    return mask.new_empty(mask.shape[0], dtype=torch.int32), mask.new_empty(mask.shape[0], dtype=torch.float32)
+
+
+@_op("length_weight_finalize")
+def length_weight_finalize(count: Tensor) -> Tensor:
+    """rel f32[n] from the gathered counts i32[n] of a sharded batch."""
+    return ops.length_weight_finalize(count)
+
+
+@length_weight_finalize.register_fake
+def _(count):
+    return count.new_empty(count.shape[0], dtype=torch.float32)
+
+
+@_op("grpo_outcome_scaled")
+def grpo_outcome_scaled(r: Tensor, mask: Tensor, seg: Tensor, eps: float, norm_by_std: bool,
+                        row_scale: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """grpo_outcome with the advantage's row scores divided by row_scale f32[B] (ret unweighted)."""
+    return ops.grpo_outcome_scaled(r, mask, seg, eps, norm_by_std, row_scale)
+
+
+@grpo_outcome_scaled.register_fake
+def _(r, mask, seg, eps, norm_by_std, row_scale):
+    return torch.empty_like(r), torch.empty_like(r)
+
+
+@_op("row_div_", ("x",))
+def row_div_(x: Tensor, scale: Tensor) -> None:
+    """x[b, :] /= scale[b] in place."""
+    ops.row_div_(x, scale)
+
+
+@row_div_.register_fake
+def _(x, scale):
+    return None
+
+
 # ============================================================= text boundary (§8(f) 2)
 def _glyphs(glyph_bytes: List[int], glyph_len: List[int]):
     import numpy as np

@@ -41,12 +41,15 @@ def compute_response_mask(data: DataProto) -> torch.Tensor:
 
 def compute_advantage(data: DataProto, adv_estimator, gamma=1.0, lam=1.0, num_repeat=1, multi_turn=False,
                       norm_adv_by_std_in_grpo=True, bi_level_gae=False, high_level_gamma=1.0, process_group=None,
-                      shard_rows=None):
+                      shard_rows=None, grpo_advantage_length_weight=False):
     """agent_trainer.py:60-137: GAE (verl, or RAGEN's bi-level), GRPO, REINFORCE++ (and its
     baseline form), REMAX and RLOO, each on the engine's kernels; an unknown estimator raises
     NotImplementedError as the reference does.  ``process_group``: the batch is this rank's
     shard and whitening uses the statistics of the whole sharded batch (core_algos); ``shard_rows``
-    (every rank's row count) makes that gather free of host synchronisation."""
+    (every rank's row count) makes that gather free of host synchronisation.
+    ``grpo_advantage_length_weight`` (GRPO only; the config key of agent_trainer.py:636-641): the
+    advantages are divided by each row's response length relative to the batch mean, in the
+    estimator's own launch; the returns stay unweighted, as in the reference."""
     pg = {"process_group": process_group, "shard_rows": shard_rows}
     _warn_rank_local("compute_advantage whitening", process_group)
     if "response_mask" not in data.batch:
@@ -64,9 +67,11 @@ def compute_advantage(data: DataProto, adv_estimator, gamma=1.0, lam=1.0, num_re
         mask = data.batch["response_mask"]
         if multi_turn:
             mask = data.batch["loss_mask"][:, -mask.size(1):]
+        rel = _relative_lengths(data.batch["response_mask"], **pg) if grpo_advantage_length_weight else None
         adv, ret = core_algos.compute_grpo_outcome_advantage(data.batch["token_level_rewards"], mask,
                                                              data.non_tensor_batch["uid"],
-                                                             norm_adv_by_std_in_grpo=norm_adv_by_std_in_grpo)
+                                                             norm_adv_by_std_in_grpo=norm_adv_by_std_in_grpo,
+                                                             row_scale=rel)
     elif est == AdvantageEstimator.REINFORCE_PLUS_PLUS_BASELINE:
         adv, ret = core_algos.compute_reinforce_plus_plus_baseline_outcome_advantage(
             data.batch["token_level_rewards"], data.batch["response_mask"], data.non_tensor_batch["uid"], **pg)
@@ -83,6 +88,30 @@ def compute_advantage(data: DataProto, adv_estimator, gamma=1.0, lam=1.0, num_re
         raise NotImplementedError
     data.batch["advantages"] = adv
     data.batch["returns"] = ret
+    return data
+
+
+def _relative_lengths(response_mask, process_group=None, shard_rows=None):
+    """(sum(response_mask, -1) + 1e-6) / sum(response_mask, -1).float().mean() (agent_trainer.py:639)
+    as f32[B] on the device.  With ``process_group`` the mean is the whole sharded batch's: the
+    row counts are gathered in global row order and finalized by the whole-batch kernel."""
+    _warn_rank_local("grpo_advantage_length_weight mean length", process_group)
+    m = core_algos._dev(response_mask, core_algos._device(response_mask))
+    count, rel = torch.ops.ragen_amd.length_weight_rows(m)
+    if process_group is None:
+        return rel
+    counts, row0 = rd.gather_row_values(count, process_group, shard_rows, with_offset=True)
+    return torch.ops.ragen_amd.length_weight_finalize(counts)[row0:row0 + count.shape[0]].contiguous()
+
+
+def apply_grpo_length_weight(data: DataProto, process_group=None, shard_rows=None):
+    """agent_trainer.py:636-641 as a step of its own, for callers that keep the reference's order
+    (compute_advantage first): advantages /= relative response lengths, per row."""
+    adv = data.batch["advantages"]
+    rel = _relative_lengths(data.batch["response_mask"], process_group, shard_rows)
+    x = core_algos._dev(adv.float(), rel.device).clone()
+    torch.ops.ragen_amd.row_div_(x, rel)
+    data.batch["advantages"] = core_algos._back(adv.device, [x])[0]
     return data
 
 

@@ -110,9 +110,11 @@ def compute_bi_level_gae_advantage_return(token_level_rewards, values, loss_mask
     return tuple(_back(token_level_rewards.device, [adv, ret], status, err, check=check, group=process_group))
 
 
-def _grouped(r, m, index, dev, run):
+def _grouped(r, m, index, dev, run, per_row=None):
     """Rows grouped by ``index`` (any hashable ids, first-seen order, as verl's id2score dict):
-    permute to contiguous groups if needed, run(rows, mask, seg) -> adv, scatter back."""
+    permute to contiguous groups if needed, run(rows, mask, seg) -> adv (a tensor or a tuple of
+    them), scatter back.  ``per_row`` (a [B] tensor) is permuted with the rows and passed to run
+    as a fourth argument."""
     groups = OrderedDict()
     for i, k in enumerate(index):
         groups.setdefault(k, []).append(i)
@@ -123,21 +125,30 @@ def _grouped(r, m, index, dev, run):
     p = None if ident else torch.from_numpy(perm).to(dev)
     rr = r if ident else r[p].contiguous()
     mm = m if ident else m[p].contiguous()
-    adv = run(rr, mm, ops.segments(seg, rr.shape[0], dev))
+    seg = ops.segments(seg, rr.shape[0], dev)
+    adv = run(rr, mm, seg) if per_row is None else run(rr, mm, seg, per_row if ident else per_row[p].contiguous())
     if not ident:
-        out = torch.empty_like(adv)
-        out[p] = adv
-        adv = out
+        def scatter(a):
+            out = torch.empty_like(a)
+            out[p] = a
+            return out
+        adv = tuple(scatter(a) for a in adv) if isinstance(adv, tuple) else scatter(adv)
     return adv
 
 
 def compute_grpo_outcome_advantage(token_level_rewards, response_mask, index, epsilon: float = 1e-6,
-                                   norm_adv_by_std_in_grpo: bool = True):
+                                   norm_adv_by_std_in_grpo: bool = True, row_scale=None):
     """verl compute_grpo_outcome_advantage: rows grouped by ``index`` (any hashable ids).
     Groups are rank-local under sharding (RAGEN's uids are unique per row, so every group has
-    one member, agent_trainer.py:551-552)."""
+    one member, agent_trainer.py:551-552).  ``row_scale`` (f32[B] on the device, the relative
+    lengths of grpo_advantage_length_weight): the advantages are divided by it per row in the
+    same launch, the returns are not (agent_trainer.py:636-641) -> (weighted adv, ret)."""
     dev = _device(token_level_rewards, response_mask)
     r, m = _dev(token_level_rewards.float(), dev), _dev(response_mask, dev)
+    if row_scale is not None:
+        adv, ret = _grouped(r, m, index, dev, lambda rr, mm, seg, sc: tuple(torch.ops.ragen_amd.grpo_outcome_scaled(
+            rr, mm, seg, float(epsilon), bool(norm_adv_by_std_in_grpo), sc)), per_row=row_scale)
+        return tuple(_back(token_level_rewards.device, [adv, ret]))
     adv = _grouped(r, m, index, dev, lambda rr, mm, seg: torch.ops.ragen_amd.grpo_outcome(
         rr, mm, seg, float(epsilon), bool(norm_adv_by_std_in_grpo))[0])
     adv = _back(token_level_rewards.device, [adv])[0]
