@@ -134,28 +134,43 @@ struct BoardTurn {
   int nes, bot;
 };
 
-// One turn: K action slots (K <= 8) of the regular room (wall, target, box; player at window
-// bit jp).  acts = the slots' action ids (byte k = slot k, each 1..8 where it is valid: the
-// caller checks), n_act <= K.  Bit-identical to exact gym_sokoban steps (the LDS path and
-// oracle/sokoban.c's sokoban_turn); box and jp are left at the turn's end.
+// The valid bytes of a turn's K action slots (slots 0..3 in lo, 4..7 in hi) for 0 <= n_act <= K,
+// the slot range formed in 32 bits.  The cached turn (sokoban_cached_turn_kernel) computes them
+// once for both the format penalty's count and the step block (board_turn_kv).
+struct ValidSlots {
+  uint32_t lo, hi;
+};
+template <int K>
+RMI_BS_FN ValidSlots valid_slots(uint32_t xl, uint32_t xh, int n_act) {
+  ValidSlots v;
+  const uint32_t rl = n_act >= 4 ? ~0u : (1u << (8 * n_act)) - 1u;
+  v.lo = valid_bytes(xl, rl);
+  v.hi = 0u;
+  if (K > 4) {
+    const int nh = n_act - 4;
+    const uint32_t rh = nh >= 4 ? ~0u : (nh <= 0 ? 0u : (1u << (8 * nh)) - 1u);
+    v.hi = valid_bytes(xh, rh);
+  }
+  return v;
+}
+
+// The turn given its action dwords and their valid bytes (valid_bytes over the slots < n_act;
+// vh is read for K > 4 only).
 template <class M, int K>
-RMI_BS_FN BoardTurn board_turn_k(M wall, M target, M& box, int& jp, int W, uint64_t acts, int n_act, int left,
-                                 int nes, int bot, int num_boxes, int max_steps) {
+RMI_BS_FN BoardTurn board_turn_kv(M wall, M target, M& box, int& jp, int W, uint32_t xl, uint32_t xh, uint32_t vl,
+                                  uint32_t vh, int left, int nes, int bot, int num_boxes, int max_steps) {
   const M box0 = box;
   const int jp0 = jp;
   // wave-uniform: the direction table (byte (id & 3) -> signed window offset)
   const uint32_t dir_table = 0x01u | ((uint32_t)(-W) & 0xFFu) << 8 | ((uint32_t)W & 0xFFu) << 16 | 0xFF000000u;
-  // per lane: the slot range, the left budget and the max_steps slot, broadcast to bytes
-  const uint64_t range = n_act >= 8 ? ~0ull : (1ull << (8 * n_act)) - 1;
+  // per lane: the left budget and the max_steps slot, broadcast to bytes
   const uint32_t l8 = left <= 0 ? 0u : (left >= 8 ? 8u : (uint32_t)left);
   const int m = max_steps - nes;  // the 1-based count of steps that ends the episode
   const uint32_t m8 = (m >= 1 && m <= 8) ? (uint32_t)m : 0x7Fu;
   const uint32_t left_b = l8 * 0x01010101u, m_b = m8 * 0x01010101u;
-  const uint32_t xl = (uint32_t)acts, xh = (uint32_t)(acts >> 32);
-  const uint32_t vl = valid_bytes(xl, (uint32_t)range);
   Slots4 q[2];
   q[0] = slots4(xl, vl, 0u, left_b, m_b, dir_table);
-  if (K > 4) q[1] = slots4(xh, valid_bytes(xh, (uint32_t)(range >> 32)), (uint32_t)popc32(vl) * 0x01010101u, left_b, m_b, dir_table);
+  if (K > 4) q[1] = slots4(xh, vh, (uint32_t)popc32(vl) * 0x01010101u, left_b, m_b, dir_table);
   // the walk: booleans are 0 / all-ones masks (selects become v_bfi), except `alive` (0 / 1:
   // the width of the slot extracts)
   uint32_t alive = 1u, taken = 0u, last_moved = 0u, z = 1u;
@@ -202,6 +217,20 @@ RMI_BS_FN BoardTurn board_turn_k(M wall, M target, M& box, int& jp, int W, uint6
   t.nes = nes + (int)taken;
   t.bot = num_boxes - open_bot;
   return t;
+}
+
+// One turn: K action slots (K <= 8) of the regular room (wall, target, box; player at window
+// bit jp).  acts = the slots' action ids (byte k = slot k, each 1..8 where it is valid: the
+// caller checks), n_act <= K.  Bit-identical to exact gym_sokoban steps (the LDS path and
+// oracle/sokoban.c's sokoban_turn); box and jp are left at the turn's end.
+template <class M, int K>
+RMI_BS_FN BoardTurn board_turn_k(M wall, M target, M& box, int& jp, int W, uint64_t acts, int n_act, int left,
+                                 int nes, int bot, int num_boxes, int max_steps) {
+  const uint64_t range = n_act >= 8 ? ~0ull : (1ull << (8 * n_act)) - 1;  // the slots < n_act
+  const uint32_t xl = (uint32_t)acts, xh = (uint32_t)(acts >> 32);
+  const uint32_t vl = valid_bytes(xl, (uint32_t)range);
+  const uint32_t vh = K > 4 ? valid_bytes(xh, (uint32_t)(range >> 32)) : 0u;
+  return board_turn_kv<M, K>(wall, target, box, jp, W, xl, xh, vl, vh, left, nes, bot, num_boxes, max_steps);
 }
 
 }  // namespace bs

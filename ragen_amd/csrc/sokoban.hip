@@ -17,6 +17,7 @@
 //      numpy's negative-index wrap, gym_sokoban's IndexError points).
 #include "common.hpp"
 #include "board_step.hpp"
+#include "lean_turn.hpp"
 #include "parse_core.hpp"
 
 #include <type_traits>
@@ -1035,6 +1036,229 @@ __global__ __launch_bounds__(kWave * kSokWpb * (kObs ? kObsFan : 1)) void sokoba
                                                          lds_fixed + (wave * kEnvs + slot) * row_words, at_end);
 }
 
+constexpr uint64_t border_cells(int H, int W) {  // bitmask of the border cells, row-major
+  uint64_t m = 0;
+  for (int r = 0; r < H; ++r)
+    for (int c = 0; c < W; ++c)
+      if (r == 0 || c == 0 || r == H - 1 || c == W - 1) m |= 1ull << (r * W + c);
+  return m;
+}
+
+// A regular room's state byte at window bit j from its boards (pl = the player's bit): player 5,
+// box 4 (3 on a target), floor 1, target 2 -- one v_perm over the table, selector
+// target | box << 1 | player << 2 (4..7 pick the 5s), no compare and no exec region per cell.
+__device__ __forceinline__ uint8_t cell_byte(uint32_t target, uint32_t box, uint32_t pl, int j) {
+  const uint32_t sel = bs::ubfe(target, (uint32_t)j, 1u) | bs::ubfe(box, (uint32_t)j, 1u) << 1 |
+                       bs::ubfe(pl, (uint32_t)j, 1u) << 2;
+  return (uint8_t)__builtin_amdgcn_perm(0x05050505u, 0x03040201u, sel);
+}
+
+// ---- the cached turn: the 6x6 one-lane layout under RMI_BOARDS_USE with everything a launch of
+// that kind never varies fixed at compile time.  At the bench's 8192 envs
+// a turn launch is one lone wave per SIMD, so its time above the launch floor is the number of
+// instructions the wave issues, and in the general kernel above most of those serve its run-time
+// generality: the cache mode, has_input, K, W, the LPE / late / 64-bit forms.  Here H = W = 6, the
+// u32 window, one lane per env, 32-bit offsets and USE are constants and K is a template parameter:
+//   - the loads are the 16-B entry, the episode scalars, n_actions and the one to three action
+//     dwords K can need (lean_turn.hpp); no row, player or counter loads, nothing zeroed for them;
+//   - one predicate before anything is stored: every acting env of the wave has a tagged entry and
+//     action ids <= 8 (a first turn: every live env's reset entry is tagged).  A wave that fails it
+//     runs the general turn_env for its envs, which loads what it needs itself, exactly as a USE
+//     wave of the general kernel falls back;
+//   - the valid-byte vectors are computed once for the penalty's count and the step block;
+//   - (r, c) comes from the final player cell, only where it is stored; the three record rows of
+//     this turn come as kernel arguments; the entry's tag is the constant 1.
+// Every output is bit-identical to the general kernel's; the addresses read and written are a
+// subset of its.
+template <int K, bool kFirst, bool kFin, bool kHasInput>
+__global__ __launch_bounds__(kWave * kSokWpb) void sokoban_cached_turn_kernel(
+    rmi_sokoban_t env_arg, rmi_episode_t ep_arg, rmi_turn_t in_arg, uint8_t* __restrict__ err_out, rmi_finalize_t fin,
+    const uint8_t* __restrict__ init_state, const int8_t* __restrict__ init_player, double* rec_reward,
+    uint8_t* rec_info, uint8_t* rec_exec) {
+  static_assert(!(kFirst && kFin), "a first turn that is also the last is launched as the general kernel");
+  using Ix = uint32_t;
+  using M = uint32_t;
+  constexpr int W = 6, HW = 36, NW = HW / 4;
+  constexpr uint32_t kWMagic = (65536u + W - 1u) / W;
+  __shared__ uint32_t lds_state[kSokWpb * kWave * NW];  // the fallback's exact path only
+  __shared__ uint32_t lds_fixed[kSokWpb * kWave * NW];
+  RMI_STAMP_DECL;
+  RMI_STAMP(0);
+  rmi_sokoban_t env = env_arg;
+  rmi_episode_t ep = ep_arg;
+  rmi_turn_t in = in_arg;
+  const uint8_t* reset_rows = init_state;
+  // (what only the first and last turns read goes first: pinned after the common list, its scalar
+  // loads were issued behind that list's wait, a second round trip ahead of the vector loads)
+  if (kFirst || kFin) args_pin(ep.T, ep.turn_reward, ep.turn_info, in.turn);
+  if (kFirst) args_pin(ep.turn_exec, reset_rows, env.init_boards);
+  if (kHasInput) args_pin(in.has_input);
+  args_pin(ep.B, env.num_boxes, env.max_steps, env.room_state, env.player, env.num_env_steps, env.boxes_on_target,
+           env.boards, ep.num_actions, ep.flags, ep.n_turns, ep.penalty, in.actions, in.n_actions,
+           in.max_actions_per_traj, in.format_penalty, rec_reward, rec_info, rec_exec);
+
+  const uint32_t B = (uint32_t)ep.B;
+  const uint32_t b = blockIdx.x * (uint32_t)(kWave * kSokWpb) + threadIdx.x;
+  const bool live = b < B;
+  const uint32_t bc = live ? b : B - 1u;
+
+  // ---- 1. the loads, issued together from clamped addresses
+  const Dw4 ent = *elem<Ix>(reinterpret_cast<const Dw4*>(kFirst ? env.init_boards : env.boards), bc);
+  uint32_t xs[NW];
+  if (kFirst) load_row<NW, 1, true>(elem<Ix>(reset_rows, bc * HW), xs, 0, NW);  // the reset row
+  uint8_t has_in = 0;
+  if (kHasInput) has_in = *elem<Ix>(in.has_input, bc);
+  uint8_t flags = 0;
+  int32_t num_actions = 0, n_turns = 0;
+  double penalty = 0.0;
+  if (!kFirst) {  // a fresh episode's record is all zero
+    flags = *elem<Ix>(ep.flags, bc);
+    num_actions = *elem<Ix>(ep.num_actions, bc);
+    n_turns = *elem<Ix>(ep.n_turns, bc);
+    penalty = *elem<Ix>(ep.penalty, bc);
+  }
+  int n_act = *elem<Ix>(in.n_actions, bc);
+  uint32_t al, ah;
+  {
+    constexpr int kN = lean::ActionLoads<K>::kDwords;
+    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(in.actions) & 3u);
+    const char* abase = (const char*)in.actions - mis;  // 4-aligned, uniform
+    const lean::ActionAddr ad = lean::action_addr<K>(bc, mis);
+    const uint32_t d0 = *(const uint32_t*)(abase + ad.o0);
+    uint32_t d1 = 0, d2 = 0;
+    if (kN >= 2) d1 = *(const uint32_t*)(abase + ad.o1);
+    if (kN >= 3) d2 = *(const uint32_t*)(abase + ad.o2);
+    lean::action_bytes<K>(d0, d1, d2, ad.sh, al, ah);
+  }
+  FinRecord rec;
+  if (kFin) rec.load<Ix>(ep, bc);
+  if (!live) flags = RMI_FLAG_DONE;
+  const bool act = live && (kHasInput ? has_in != 0 : !(flags & RMI_FLAG_DONE));
+
+  // ---- 2. the valid slots, and the predicate of the lean path
+  if (n_act > K) n_act = K;
+  const bs::ValidSlots vs = bs::valid_slots<K>(al, ah, n_act);
+  const bool acts_ok = ((gt8_bytes(al) & vs.lo) | (K > 4 ? gt8_bytes(ah) & vs.hi : 0u)) == 0;
+  const bool tagged = (ent.w >> 8 & 0xFFu) == 1u;
+  const int lean_ok = kFirst ? (!live) | (tagged & (acts_ok | !act)) : (!act) | (tagged & acts_ok);
+  // what only the lean path reads is used here, so that its loads stay with the others above: left
+  // to the compiler they sink past the branch below to their first use, a second memory round trip
+  if (kFirst) {
+#pragma unroll
+    for (int i = 0; i < NW; ++i) asm volatile("" : "+v"(xs[i]));
+  } else {
+    asm volatile("" : "+v"(num_actions), "+v"(n_turns), "+v"(penalty));
+  }
+  if (__builtin_expect(!__all(lean_ok), 0)) {
+    // rare: this wave's envs take the general turn (nothing has been stored yet)
+    constexpr uint64_t kBorder = border_cells(W, W);
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    turn_env<HW, M, 1, kFin, kFirst, false, true, Ix, false>(
+        env_arg, ep_arg, in_arg, HW, kWMagic, kBorder, err_out, fin, init_state, init_player, (int64_t)b, 0,
+        lds_state + (wave * kWave + lane) * NW, lds_fixed + (wave * kWave + lane) * NW,
+        [](const auto&, const auto&, M, M, M, int) {});
+    return;
+  }
+  RMI_STAMP_WAIT(1);
+  if (kFirst && live) store_row<NW, 1, true>(elem<Ix>(env.room_state, b * HW), xs, 0, NW);  // the reset
+
+  M wall = ent.x, target = ent.y, box = ent.z;
+  int jp = (int)(ent.w & 0xFFu) - W;
+  int nes = (int)(ent.w >> 16 & 0xFFu), bot = (int)(int8_t)(ent.w >> 24);
+  RMI_STAMP(2);
+
+  // ---- 3. the turn and its outputs
+  double acc = 0.0;
+  uint8_t info = 0;
+  uint32_t taken = 0;
+  if (act) {
+    flags &= (uint8_t)~RMI_FLAG_DONE;
+    const int nv = __popc(vs.lo) + (K > 4 ? __popc(vs.hi) : 0);
+    if (nv != n_act || nv == 0) penalty += in.format_penalty;
+    const int left = in.max_actions_per_traj - num_actions;
+    const M box0 = box;
+    const int jp0 = jp;
+    const BoardTurn t = bs::board_turn_kv<M, K>(wall, target, box, jp, W, al, ah, vs.lo, vs.hi, left, nes, bot,
+                                                env.num_boxes, env.max_steps);
+    nes = t.nes;
+    bot = t.bot;
+    acc = t.acc;
+    info = (uint8_t)t.info;
+    taken = t.taken;
+    if (t.moved) {
+      // the changed cells, as turn_env stores them: the old and new player cells and the cells whose
+      // box bit flipped; the first 4 straight-line (a missing one repeats the first)
+      const M pl = (M)1 << jp;
+      M m = (box0 ^ box) | ((M)1 << jp0) | pl;
+      const uint32_t win = b * HW + W;  // window bit j = cell W + j
+      int jj[4];
+      jj[0] = __builtin_ctz(m);
+      m &= m - 1;
+#pragma unroll
+      for (int k = 1; k < 4; ++k) {
+        jj[k] = m ? __builtin_ctz(m) : jj[0];
+        m &= m - 1;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) *elem<Ix>(env.room_state, win + jj[k]) = cell_byte(target, box, pl, jj[k]);
+      while (m) {  // a turn that moved several boxes
+        const int j = __builtin_ctz(m);
+        m &= m - 1;
+        *elem<Ix>(env.room_state, win + j) = cell_byte(target, box, pl, j);
+      }
+    }
+    // end of the turn (finish_turn)
+    num_actions += (int32_t)taken;
+    n_turns += 1;
+    if (t.stop) {
+      flags |= RMI_FLAG_TERMINATED | RMI_FLAG_DONE;
+      flags = t.succ ? (uint8_t)(flags & ~RMI_FLAG_TRUNCATED) : (uint8_t)(flags | RMI_FLAG_TRUNCATED);
+    } else if (num_actions >= in.max_actions_per_traj) {
+      flags |= RMI_FLAG_TERMINATED | RMI_FLAG_TRUNCATED | RMI_FLAG_DONE;
+    }
+    *elem<Ix>(ep.num_actions, b) = num_actions;
+    *elem<Ix>(ep.flags, b) = flags;
+    *elem<Ix>(ep.n_turns, b) = n_turns;
+    *elem<Ix>(ep.penalty, b) = penalty;
+    *elem<Ix>(rec_reward, b) = acc;
+    *elem<Ix>(rec_info, b) = info;
+    *elem<Ix>(rec_exec, b) = (uint8_t)taken;
+  }
+  RMI_STAMP(3);
+  if (kFirst ? live : (act && taken != 0)) {
+    // the player and the counters: a first turn writes every live env's (the reset's where the env
+    // did not act), a later turn those of the envs that executed an action
+    const uint32_t p = (uint32_t)(jp + W);
+    const uint32_t r = (p * kWMagic) >> 16, c = p - r * W;
+    *elem<Ix>(reinterpret_cast<uint16_t*>(env.player), b) = (uint16_t)(r | c << 8);
+    *elem<Ix>(env.num_env_steps, b) = nes;
+    *elem<Ix>(env.boxes_on_target, b) = bot;
+  }
+  if (kFirst && live) {
+    if (!act) {  // no input this turn: the env keeps its reset state
+      *elem<Ix>(ep.num_actions, b) = 0;
+      *elem<Ix>(ep.flags, b) = 0;
+      *elem<Ix>(ep.n_turns, b) = 0;
+      *elem<Ix>(ep.penalty, b) = 0.0;
+    }
+    for (int t = 0; t < ep.T; ++t)
+      if (t != in.turn || !act) {
+        *elem<Ix>(ep.turn_reward + (int64_t)t * B, b) = 0.0;
+        *elem<Ix>(ep.turn_info + (int64_t)t * B, b) = 0;
+        *elem<Ix>(ep.turn_exec + (int64_t)t * B, b) = 0;
+      }
+  }
+  if (kFirst ? live : act)  // the entry after the turn: stepped on its boards, so it stays tagged
+    *elem<Ix>(reinterpret_cast<Dw4*>(env.boards), b) =
+        Dw4{wall, target, box, ((uint32_t)(jp + W) & 0xFFu) | 1u << 8 | ((uint32_t)nes & 0xFFu) << 16 |
+                                   ((uint32_t)bot & 0xFFu) << 24};
+  RMI_STAMP(4);
+  if (kFin) {
+    if (act) rec.set(in.turn, acc, info);  // this turn's record is still in registers
+    finalize_envs<1, Ix>(ep, fin, rec, b, live, flags, n_turns, num_actions, penalty, act ? in.turn : -1, acc, info);
+  }
+}
+
 // Fused reset: room_state/player from the generated rooms, counters and the whole episode
 // record zeroed, in one launch (SokobanEnv.reset sokoban/env.py:37-38 + EnvStatus()).
 __global__ __launch_bounds__(kBlock) void sokoban_reset_kernel(rmi_sokoban_t env, rmi_episode_t ep, int hw,
@@ -1308,6 +1532,32 @@ namespace {
 // launcher passes it instead of every wave dividing
 inline uint32_t w_magic_of(int W) { return (65536u + (uint32_t)W - 1u) / (uint32_t)W; }
 
+// The cached turn's launch: K and has_input select the instantiation; the three record rows of
+// in->turn are passed as arguments.
+template <bool kFin, bool kFirst, bool kHasInput>
+void cached_turn_launch(const rmi_sokoban_t* env, const rmi_episode_t* ep, const rmi_turn_t* in, uint8_t* err,
+                        const rmi_finalize_t& fin, hipStream_t s, const uint8_t* init_state, const int8_t* init_player,
+                        unsigned grid) {
+  const int64_t tb = (int64_t)in->turn * ep->B;
+#define RMI_CACHED_K(k_)                                                                                          \
+  case k_:                                                                                                        \
+    hipLaunchKernelGGL((sokoban_cached_turn_kernel<k_, kFirst, kFin, kHasInput>), dim3(grid), dim3(kWave * kSokWpb), \
+                       0, s, *env, *ep, *in, err, fin, init_state, init_player, ep->turn_reward + tb,              \
+                       ep->turn_info + tb, ep->turn_exec + tb);                                                    \
+    break;
+  switch (in->K) {
+    RMI_CACHED_K(1)
+    RMI_CACHED_K(2)
+    RMI_CACHED_K(3)
+    RMI_CACHED_K(4)
+    RMI_CACHED_K(5)
+    RMI_CACHED_K(6)
+    RMI_CACHED_K(7)
+    RMI_CACHED_K(8)
+  }
+#undef RMI_CACHED_K
+}
+
 template <bool kFin, bool kFirst = false>
 int sokoban_step_turn_launch(const rmi_sokoban_t* env, const rmi_episode_t* ep, const rmi_turn_t* in, uint8_t* err,
                              const rmi_finalize_t& fin, hipStream_t s, const uint8_t* init_state = nullptr,
@@ -1329,6 +1579,15 @@ int sokoban_step_turn_launch(const rmi_sokoban_t* env, const rmi_episode_t* ep, 
                       (env->boards_mode != RMI_BOARDS_BUILD && env->boards_mode != RMI_BOARDS_USE) ||
                       ((reinterpret_cast<uintptr_t>(env->boards) | reinterpret_cast<uintptr_t>(env->init_boards)) & 15u)))
     return RMI_EUNSUP;
+  // the 6x6 one-lane layout reading a built cache: the cached turn (sokoban_cached_turn_kernel)
+  if (H == 6 && W == 6 && !spread && ep->B < RMI_SOK_LATE_MIN && ep->B < kOff32MaxB && env->boards &&
+      env->boards_mode == RMI_BOARDS_USE && (!kFirst || env->init_boards) && in->K >= 1) {
+    if (in->has_input)
+      cached_turn_launch<kFin, kFirst, true>(env, ep, in, err, fin, s, init_state, init_player, grid);
+    else
+      cached_turn_launch<kFin, kFirst, false>(env, ep, in, err, fin, s, init_state, init_player, grid);
+    return launch_status();
+  }
 #define RMI_LAUNCH(HW_, M_)                                                                                   \
   do {                                                                                                        \
     if (spread)                                                                                               \

@@ -17,11 +17,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--envs", type=int, default=8192)
+    ap.add_argument("--fused", action="store_true",
+                    help="the bench's own sequence: fused first turn, plain turns, fused last turn")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     R = Rollout(dev, 0, B=a.envs)
     for _ in range(a.reps):
-        R.step_unfused()  # T plain turn launches: the per-launch counters of the turn kernel alone
+        if a.fused:
+            R.step()
+        else:
+            R.step_unfused()  # T plain turn launches: the per-launch counters of the turn kernel alone
     torch.cuda.synchronize()
     print("steps per rollout", int(R.env.ep.turn_exec.sum().item()))
 
